@@ -15,11 +15,21 @@ reference-scheme init.  Weak scaling: every rank processes its own 24 images.
 
 Rank 0 prints ONE JSON line.  `value` / `ms_per_step` are the wall clock of exactly K steps between barriers
 (the driver's contract); `ms_per_step_median` is the median of the K per-step times taken from events on the
-stream.  `roofline` describes the dominant kernel class of the caller's stream (the critical path; chosen from a
+stream.
+
+A plain run does only what that headline needs: set-up, W warm-up steps, the K timed steps, the line.  `--dump-outputs DIR` then
+writes what the last timed step computed (dump_outputs below); in such a run the last train step starts from the seeded initial
+state again (measure(): state0), so that two runs -- or two builds -- compute it from the same parameters.  Everything else the
+line can carry -- `roofline`, `also`, `cpu_baseline` -- takes work of its own (a profiled warm-up step, per-class events in the
+timed region, extra runs) and is measured with `--full` only:
+
+  python bench.py --gpus 1 --steps 20 --warmup 5 --full
+
+With --full, `roofline` describes the dominant kernel class of the caller's stream (the critical path; chosen from a
 profiled warm-up step; a larger side-stream class, if any, is named in `roofline.largest_side_stream_class`):
 achieved = algorithmic FLOPs of its launches / their HIP-event time measured inside the timed region on the
 launch stream.  `cpu_baseline` times the CPU oracle (oracle/cunet_ref.py, a restatement of the reference pinned
-bit-exact to it) on this host for a bounded sample.  At N=1 the same run also times the other single-GPU
+bit-exact to it) on this host for a bounded sample.  At N=1 a --full run also times the other single-GPU
 headline configurations of BASELINE.json -- config 3 (CU-Net-8, bf16 storage), config 5 (CU-Net-16, binary weights; MFMA and
 AND-popcount forward) -- and the forward-only (inference) rates, attached as `also: [...]` (BASELINE's metric names "CU-Net-2 and
 CU-Net-8"); at N > 1 the `also` entries are BASELINE config 4 (CU-Net-8, K = 16, 24 images per rank, RCCL all-reduce).
@@ -174,61 +184,50 @@ def coll_device(pg, dev):
     return torch.device('cpu') if dist.get_backend(pg) == 'gloo' else dev
 
 
-def measure(dev, pg, rank, world, L, K, bs, steps, warmup, mode='fp32', bits_w=0, forward_only=False, popcount=False,
-            profile_out='', seed=2, serial=False, force_class=None):
-    """Time `steps` steps of one workload.  mode: 'fp32' | 'bf16' (activations) | 'bf16_grads' (+ gradient tensors).
-    serial: build the plan with CUNET_NO_SIDE_STREAM (weight gradients on the caller's stream, so every kernel runs ALONE on
-    the GPU): the per-launch durations of a class are then the kernel's own, not its share of a GPU it co-occupies."""
-    import cu_net_amd
-    from cu_net_amd.trainer import FusedTrainer
-    bf16 = mode != 'fp32'
-    torch.manual_seed(seed)
-    net = cu_net_amd.create_cu_net(neck_size=4, growth_rate=32, init_chan_num=128, class_num=K,
-                                   layer_num=L, order=1, loss_num=L).to(dev)
-    net.train()
-    quan = None
-    if bits_w > 0:
-        from cu_net_amd.quant import QuanOp
-        quan = QuanOp(net, bits_w=bits_w, bits_i=8, bits_g=8)
-    kw = {}
-    if popcount:
-        kw['popcount'] = True
-    tr = FusedTrainer(net, lr=2.5e-4, alpha=0.99, eps=1e-8, process_group=pg, quan_op=quan, bf16=bf16,
-                      bf16_grads=mode == 'bf16_grads', **kw)
-    tr.broadcast_parameters(0)
-    x, t = synthetic_batch(bs, K, 256, seed=1000 + rank, device=dev)
+DUMP_BUDGET_BYTES = 64 * 10 ** 6      # --dump-outputs: all files together, npy headers included
+DUMP_SAMPLE_SEED = 0
 
-    def barrier():
-        torch.cuda.synchronize(dev)
-        if pg is not None:
-            import torch.distributed as dist
-            dist.barrier()
-        torch.cuda.synchronize(dev)
 
-    if forward_only:
-        net.eval()
+def dump_outputs(out_dir, arrays):
+    """Write {name: tensor} as out_dir/<name>.npy: float64 tensors as float64, everything else as float32.  If the whole set is
+    larger than DUMP_BUDGET_BYTES, the largest arrays are cut to a fixed sample of their flattened elements -- indices drawn once
+    from a generator seeded with DUMP_SAMPLE_SEED, sorted -- with the budget shared out so that smaller arrays stay whole.  The
+    same arguments therefore give the same files, element for element, on any build."""
+    import numpy as np
+    host = {k: (v.detach().double() if v.dtype == torch.float64 else v.detach().float()).reshape(-1 if v.dim() else 1).cpu()
+            for k, v in arrays.items()}
+    size = {k: v.numel() * v.element_size() for k, v in host.items()}
+    keep = dict(size)
+    left, todo = DUMP_BUDGET_BYTES - 256 * len(host), sorted(size, key=lambda k: size[k])      # (256: room for each npy header)
+    while todo:      # water-filling: an array within its fair share of what is left is kept whole, the rest share the remainder
+        share = left // len(todo)
+        k = todo[0]
+        if size[k] <= share:
+            left -= size[k]
+            todo.pop(0)
+            continue
+        for k in todo:
+            keep[k] = share
+        break
+    os.makedirs(out_dir, exist_ok=True)
+    total = 0
+    for k, v in host.items():
+        n = keep[k] // v.element_size()
+        if n < v.numel():
+            idx = np.sort(np.random.default_rng(DUMP_SAMPLE_SEED).choice(v.numel(), size=n, replace=False))
+            a = v.numpy()[idx]
+        else:
+            a = v.numpy().reshape(tuple(arrays[k].shape))
+        np.save(os.path.join(out_dir, k + '.npy'), a)
+        total += a.nbytes
+        log(f'dump: {k} {tuple(arrays[k].shape)} -> {a.shape} {a.dtype}' + (' (seeded sample)' if n < v.numel() else ''))
+    log(f'dump: {len(host)} arrays, {total / 1e6:.1f} MB in {out_dir}')
 
-        def one_step():
-            with torch.no_grad():
-                outs = net.forward_bf16(x) if bf16 else net(x)      # the public path: loss_num NCHW heat maps
-            return outs[-1][0, 0, 0, 0]
-    else:
-        def one_step():
-            return tr.step(x, t)
-    if serial:
-        os.environ['CUNET_NO_SIDE_STREAM'] = '1'       # read when the plan handle is created
-    try:
-        plan = net._get_plan(bs, 256, 256, not forward_only, bf16=bf16)
-    finally:
-        if serial:
-            del os.environ['CUNET_NO_SIDE_STREAM']
-    # ---- warm-up; the last warm-up step is profiled per kernel class to pick the dominant one
-    for i in range(max(warmup, 1)):
-        if i == max(warmup, 1) - 1:
-            plan.handle.profile_reset()
-            plan.handle.profile_begin(1)
-        loss = one_step()
-    torch.cuda.synchronize(dev)
+
+def warmup_profile(plan, rank, L, K, mode, bits_w, profile_out, serial, force_class):
+    """After the profiled warm-up step of measure(): the roofline class, the profile stream to read it from, whether the library
+    recorded classes at all, and the note on a larger side-stream class.  Rank 0 logs the per-class table (and appends it to
+    profile_out)."""
     prof_all = plan.handle.profile_collect()
     prof_main = plan.handle.profile_collect(0)      # launches on the caller's stream only
     prof_side = plan.handle.profile_collect(1)      # launches on the library's side stream only
@@ -256,42 +255,12 @@ def measure(dev, pg, rank, world, L, K, bs, steps, warmup, mode='fp32', bits_w=0
         if profile_out:
             with open(profile_out, 'a') as f:
                 f.write('\n'.join(lines) + '\n')
+    return dominant, which, have_classes, side_note
 
-    # ---- timed region: exactly `steps` steps; HIP events only around the dominant class, one event per step
-    # A timed HIP event is a marker packet on the stream and the kernel behind it waits for it to retire: ~6 us per event when the
-    # class runs on the caller's stream (the 1x1 data gradient: 47 launches x 2 events = 0.5 ms of a 7.2 ms CU-Net-2 step, ~1.2 ms
-    # of a CU-Net-8 step).  The dominant class is therefore bracketed in TWO steps of the timed region only (the first and the
-    # middle one): its average launch duration is still measured live, inside the timed region, on the stream the kernel runs on,
-    # over ~100 - 500 launches, and `value` is not taxed by the measurement.
-    EVENT_STRIDE = max(4, steps // 2)
-    plan.handle.profile_reset()
-    cls_index = plan.handle.profile_class_index(dominant)
-    use_events = not os.environ.get('CUNET_BENCH_NO_CLASS_EVENTS')      # (tools only: how much do the per-launch events cost?)
-    evs = [torch.cuda.Event(enable_timing=True) for _ in range(steps + 1)]
-    barrier()
-    t0 = time.perf_counter()
-    evs[0].record()
-    for i in range(steps):
-        if use_events:
-            plan.handle.profile_begin(2 if i % EVENT_STRIDE == 0 else 0, cls_index)
-        loss = one_step()
-        evs[i + 1].record()
-    barrier()
-    dt = time.perf_counter() - t0
-    prof = plan.handle.profile_collect(which)
-    plan.handle.profile_begin(0)
-    per_step = [evs[i].elapsed_time(evs[i + 1]) for i in range(steps)]
-    if pg is not None:
-        import torch.distributed as dist
-        tt = torch.tensor([dt], dtype=torch.float64, device=coll_device(pg, dev))
-        dist.all_reduce(tt, op=dist.ReduceOp.MAX)
-        dt = float(tt.item())
-    res = {'dt': dt, 'final_loss': float(loss), 'per_step_ms': per_step}
-    imgs = world * bs * steps
-    value = imgs / dt
-    res['value'] = value
-    res['ms_per_step'] = 1e3 * dt / steps
-    res['ms_per_step_median'] = statistics.median(per_step)
+
+def roofline_of(prof, dominant, have_classes, side_note, bf16, mode, L, K, bs):
+    """The `roofline` entry of measure(): the dominant class's launches in the timed region (`prof`) against the roof that bounds
+    it, with the committed PMC figures of this workload where there are some (None when the library recorded no classes)."""
     cnt, ms, fl, by = prof[dominant]
     peak_mfma = PEAK_BF16_MFMA_TFLOPS if dominant.endswith('_bf16') else PEAK_F32_MFMA_TFLOPS      # classes that run on bf16 MFMA carry the suffix
     # fp32 convolution classes on the split contraction (F32_SPLIT): six bf16 products per fp32 product -- the matrix-pipe ceiling of the
@@ -337,7 +306,125 @@ def measure(dev, pg, rank, world, L, K, bs, steps, warmup, mode='fp32', bits_w=0
             roof['mfma_busy_source'] = msrc
         if side_note:
             roof['largest_side_stream_class'] = side_note
-    res['roofline'] = roof
+    return roof
+
+
+def measure(dev, pg, rank, world, L, K, bs, steps, warmup, mode='fp32', bits_w=0, forward_only=False, popcount=False,
+            profile_out='', seed=2, serial=False, force_class=None, roofline=True, dump_dir=''):
+    """Time `steps` steps of one workload.  mode: 'fp32' | 'bf16' (activations) | 'bf16_grads' (+ gradient tensors).
+    serial: build the plan with CUNET_NO_SIDE_STREAM (weight gradients on the caller's stream, so every kernel runs ALONE on
+    the GPU): the per-launch durations of a class are then the kernel's own, not its share of a GPU it co-occupies.
+    roofline: profile the last warm-up step per kernel class and time the dominant class inside the timed region (`--full`);
+    without it the warm-up and the timed steps run bare and the result has no `roofline`.
+    dump_dir: on rank 0, write what the last timed step computed to dump_dir (dump_outputs)."""
+    import cu_net_amd
+    from cu_net_amd.trainer import FusedTrainer
+    bf16 = mode != 'fp32'
+    torch.manual_seed(seed)
+    net = cu_net_amd.create_cu_net(neck_size=4, growth_rate=32, init_chan_num=128, class_num=K,
+                                   layer_num=L, order=1, loss_num=L).to(dev)
+    net.train()
+    quan = None
+    if bits_w > 0:
+        from cu_net_amd.quant import QuanOp
+        quan = QuanOp(net, bits_w=bits_w, bits_i=8, bits_g=8)
+    kw = {}
+    if popcount:
+        kw['popcount'] = True
+    tr = FusedTrainer(net, lr=2.5e-4, alpha=0.99, eps=1e-8, process_group=pg, quan_op=quan, bf16=bf16,
+                      bf16_grads=mode == 'bf16_grads', **kw)
+    tr.broadcast_parameters(0)
+    x, t = synthetic_batch(bs, K, 256, seed=1000 + rank, device=dev)
+    # --dump-outputs: the LAST timed train step starts again from this seeded state (parameters, BatchNorm buffers and counters, an
+    # empty RMSprop state), so what it computes is a function of the arguments alone.  Carried over from the steps before it, the
+    # last-bit run-to-run differences of the float atomics in the weight gradients would not stay small: RMSprop's first steps move
+    # a parameter by ~10 x lr whatever its gradient's size, and within a few steps two runs' heat maps differ visibly.
+    state0 = None
+    if dump_dir and not forward_only:
+        state0 = [a.clone() for a in (net._param_arena, net._buffer_arena, net._counter_arena)]
+
+    def barrier():
+        torch.cuda.synchronize(dev)
+        if pg is not None:
+            import torch.distributed as dist
+            dist.barrier()
+        torch.cuda.synchronize(dev)
+
+    last = {}
+    if forward_only:
+        net.eval()
+
+        def one_step():
+            with torch.no_grad():
+                outs = net.forward_bf16(x) if bf16 else net(x)      # the public path: loss_num NCHW heat maps
+            if dump_dir:
+                last['outs'] = outs
+            return outs[-1][0, 0, 0, 0]
+    else:
+        def one_step():
+            return tr.step(x, t)
+    if serial:
+        os.environ['CUNET_NO_SIDE_STREAM'] = '1'       # read when the plan handle is created
+    try:
+        plan = net._get_plan(bs, 256, 256, not forward_only, bf16=bf16)
+    finally:
+        if serial:
+            del os.environ['CUNET_NO_SIDE_STREAM']
+    # ---- warm-up; with `roofline` the last warm-up step is profiled per kernel class to pick the dominant one
+    for i in range(max(warmup, 1)):
+        if roofline and i == max(warmup, 1) - 1:
+            plan.handle.profile_reset()
+            plan.handle.profile_begin(1)
+        loss = one_step()
+    torch.cuda.synchronize(dev)
+    if roofline:
+        dominant, which, have_classes, side_note = warmup_profile(plan, rank, L, K, mode, bits_w, profile_out, serial, force_class)
+    # ---- timed region: exactly `steps` steps; HIP events only around the dominant class, one event per step
+    # A timed HIP event is a marker packet on the stream and the kernel behind it waits for it to retire: ~6 us per event when the
+    # class runs on the caller's stream (the 1x1 data gradient: 47 launches x 2 events = 0.5 ms of a 7.2 ms CU-Net-2 step, ~1.2 ms
+    # of a CU-Net-8 step).  The dominant class is therefore bracketed in TWO steps of the timed region only (the first and the
+    # middle one): its average launch duration is still measured live, inside the timed region, on the stream the kernel runs on,
+    # over ~100 - 500 launches, and `value` is not taxed by the measurement.
+    # Without `roofline` the timed steps carry no class events (nor the per-launch profile records behind them).
+    use_events = roofline and not os.environ.get('CUNET_BENCH_NO_CLASS_EVENTS')      # (tools only: how much do the per-launch events cost?)
+    if roofline:
+        EVENT_STRIDE = max(4, steps // 2)
+        plan.handle.profile_reset()
+        cls_index = plan.handle.profile_class_index(dominant)
+    evs = [torch.cuda.Event(enable_timing=True) for _ in range(steps + 1)]
+    barrier()
+    t0 = time.perf_counter()
+    evs[0].record()
+    for i in range(steps):
+        if use_events:
+            plan.handle.profile_begin(2 if i % EVENT_STRIDE == 0 else 0, cls_index)
+        if state0 is not None and i == steps - 1:      # (device-to-device copies on the step's stream: ~16 MB at CU-Net-2)
+            for a, a0 in zip((net._param_arena, net._buffer_arena, net._counter_arena), state0):
+                a.copy_(a0)
+            if tr.square_avg is not None:
+                tr.square_avg.zero_()
+            tr.steps_done = 0
+        loss = one_step()
+        evs[i + 1].record()
+    barrier()
+    dt = time.perf_counter() - t0
+    if roofline:
+        prof = plan.handle.profile_collect(which)
+        plan.handle.profile_begin(0)
+    per_step = [evs[i].elapsed_time(evs[i + 1]) for i in range(steps)]
+    if pg is not None:
+        import torch.distributed as dist
+        tt = torch.tensor([dt], dtype=torch.float64, device=coll_device(pg, dev))
+        dist.all_reduce(tt, op=dist.ReduceOp.MAX)
+        dt = float(tt.item())
+    res = {'dt': dt, 'final_loss': float(loss), 'per_step_ms': per_step}
+    imgs = world * bs * steps
+    value = imgs / dt
+    res['value'] = value
+    res['ms_per_step'] = 1e3 * dt / steps
+    res['ms_per_step_median'] = statistics.median(per_step)
+    if roofline:
+        res['roofline'] = roofline_of(prof, dominant, have_classes, side_note, bf16, mode, L, K, bs)
     g = (FWD_GFLOP_PER_IMG if forward_only else TRAIN_GFLOP_PER_IMG).get((L, K))
     if g:
         res['step_tflops'] = round(g * value / 1e3, 2)
@@ -350,6 +437,15 @@ def measure(dev, pg, rank, world, L, K, bs, steps, warmup, mode='fp32', bits_w=0
         mb = fb * (0.5 if bf16 else 1.0) * (1.0 if forward_only else 3.0)
         res['step_algorithmic_GBs'] = round(mb * value / 1e3, 1)
         res['step_frac_of_hbm_peak'] = round(mb * value / 1e3 / (PEAK_HBM_GBS * world), 4)
+    if dump_dir and rank == 0:
+        # what a caller of the timed path holds after its last step: the heat maps of every head (NCHW) and, for a train step,
+        # the loss and the module's state after the RMSprop update (parameters, BatchNorm running statistics and counters) -- of
+        # one step from the seeded state (state0 above)
+        heads = last['outs'] if forward_only else tr.last_outputs(x.shape)
+        arrays = {f'heatmap_{i}': h for i, h in enumerate(heads)}
+        if not forward_only:
+            arrays.update(loss=loss, params=net._param_arena, buffers=net._buffer_arena, counters=net._counter_arena.double())
+        dump_outputs(dump_dir, arrays)
     del tr, net, plan
     torch.cuda.empty_cache()
     return res
@@ -387,6 +483,11 @@ def main():
     ap.add_argument('--layers', type=int, default=2)
     ap.add_argument('--class-num', type=int, default=68)
     ap.add_argument('--bs', type=int, default=24, help='per-GPU batch')
+    ap.add_argument('--dump-outputs', default='', metavar='DIR',
+                    help='after the timed steps, write what the last one computed as DIR/<name>.npy (float32 / float64, <= 64 MB in all)')
+    ap.add_argument('--full', action='store_true', help='also measure what the headline does not need: `roofline` (profiled warm-up step, '
+                    'class events in the timed region, the side-stream-off pass), the `also` configurations and the CPU baseline; '
+                    'the --no-* / --also-steps / --cpu-steps / --profile-out options below refine a --full run')
     ap.add_argument('--cpu-steps', type=int, default=20, help='timed steps of the CPU baseline at its best thread count (5 warm-up steps in front)')
     ap.add_argument('--no-cpu-baseline', action='store_true')
     ap.add_argument('--no-also', action='store_true', help='skip the extra CU-Net-8 bf16 / CU-Net-16 binary-weight lines')
@@ -471,9 +572,9 @@ def main():
     mode = 'bf16_grads' if args.bf16_grads else ('bf16' if args.bf16 else 'fp32')
     is_default = (L, K, bs, mode, args.bits_w, args.forward_only, args.popcount) == (2, 68, 24, 'fp32', 0, False, False)
     r = measure(dev, pg, rank, world, L, K, bs, args.steps, args.warmup, mode, args.bits_w, args.forward_only,
-                args.popcount, args.profile_out)
+                args.popcount, args.profile_out, roofline=args.full, dump_dir=args.dump_outputs)
     alone = None
-    if world == 1 and is_default and r['roofline'] and not args.no_alone and 'CUNET_NO_SIDE_STREAM' not in os.environ:
+    if args.full and world == 1 and is_default and r['roofline'] and not args.no_alone and 'CUNET_NO_SIDE_STREAM' not in os.environ:
         # the same class timed with nothing else on the GPU (outside the timed region; a separate plan without the side stream)
         try:
             a = measure(dev, None, 0, 1, L, K, bs, 8, 3, mode, args.bits_w, False, args.popcount, serial=True,
@@ -499,7 +600,7 @@ def main():
             'ranks_seen_by_rccl': ranks_seen,
             'backend': 'rccl' if backend == 'nccl' else 'gloo (host-staged: not a measurement)',
             'library_path': os.path.relpath(cu_net_amd._lib.LIB_PATH, ROOT),
-            'roofline': r['roofline'],
+            **({'roofline': r['roofline']} if args.full else {}),
             'final_loss': r['final_loss'],
         }
         if mode == 'fp32':
@@ -515,7 +616,7 @@ def main():
     #      N = 1: configs[2] (CU-Net-8, bf16 storage), configs[4] (CU-Net-16, binary weights; MFMA and AND-popcount forward) and
     #             the forward-only (inference) rates of the bench workload (SURVEY 8d "also forward-only img/s");
     #      N > 1: configs[3] (CU-Net-8, K = 16, 24 images per rank, bucketed RCCL all-reduce) -- every rank takes part.
-    if is_default and not args.no_also:
+    if args.full and is_default and not args.no_also:
         also = []
         if world == 1:
             extra = [(8, 68, 'bf16_grads', 0, False, False), (16, 16, 'fp32', 1, False, False), (16, 16, 'fp32', 1, True, False),
@@ -554,7 +655,7 @@ def main():
         if rank == 0:
             out['also'] = also
     if rank == 0:
-        if world == 1 and not args.no_cpu_baseline and not args.forward_only:
+        if args.full and world == 1 and not args.no_cpu_baseline and not args.forward_only:
             out['cpu_baseline'] = cpu_baseline(L, K, args.cpu_steps)
         print(json.dumps(out), flush=True)
     if world > 1 or pg is not None:

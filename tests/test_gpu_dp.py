@@ -194,7 +194,7 @@ def test_bench_two_ranks_end_to_end():
         env.pop(k, None)
     rccl = torch.cuda.device_count() >= 2
     env['CUNET_BENCH_BACKEND'] = 'nccl' if rccl else 'gloo'
-    cmd = [sys.executable, os.path.join(ROOT, 'bench.py'), '--gpus', '2', '--steps', '3', '--warmup', '1', '--also-steps', '2',
+    cmd = [sys.executable, os.path.join(ROOT, 'bench.py'), '--gpus', '2', '--steps', '3', '--warmup', '1', '--full', '--also-steps', '2',
            '--no-cpu-baseline', '--no-alone']
     r = subprocess.run(cmd, env=env, cwd=ROOT, capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, r.stdout[-3000:] + r.stderr[-3000:]

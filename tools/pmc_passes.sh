@@ -4,7 +4,7 @@ set -u
 TAG=$1; shift
 ROOT=$(pwd)
 export TMPDIR=/tmp
-BENCH="python $ROOT/bench.py --steps 2 --warmup 1 --no-cpu-baseline"
+BENCH="python $ROOT/bench.py --steps 2 --warmup 1 --full --no-cpu-baseline"
 cd /tmp
 i=0
 for set in "SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY SQ_VALU_MFMA_BUSY_CYCLES SQ_ACTIVE_INST_VMEM SQ_INST_LEVEL_VMEM" \
